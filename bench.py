@@ -24,10 +24,25 @@ K steps are timed between barrier + device synchronize; rank 0 prints ONE JSON l
 (max time over ranks).  Data: synthetic stereo pairs; weights: seeded random init of the upstream
 architecture.
 
-Also reported (rank 0, extra fields): the all-gather alone (ms per step, measured after the timed region),
-the rank -> device map, the engine's device footprint, and — single-process runs only — batch-1 latency in
-the reference's timed region (pinned copy, H2D, network, reprojection, D2H of disparity + point cloud;
-RAFTStereo/src/TRTRAFTStereo.cpp:119-146) for every model preset.
+A plain run does only that: set up, warm up, time the K steps, print the line (rank 0 extra fields: the rank ->
+device map, the engine's device footprint, the tactic plan).  ``--full`` adds the measurements that take runs of
+their own: the all-gather alone (ms per step, measured after the timed region) and — single-process runs only,
+unless ``--no-latency`` — batch-1 latency in the reference's timed region (pinned copy, H2D, network,
+reprojection, D2H of disparity + point cloud; RAFTStereo/src/TRTRAFTStereo.cpp:119-146) for every model preset.
+
+``--dump-outputs DIR`` (rank 0) writes what the last timed step returned to its caller as float32 ``.npy`` files:
+``DIR/disparity.npy`` (the gathered disparity maps, [world * B, H, W]) and the rank's point cloud, whole as
+``DIR/cloud.npy`` ([B, H, W, 6]) when its share of DUMP_BUDGET bytes covers it, otherwise (the default 8 x 480 x
+640) ``DIR/cloud_sample.npy`` ([n, 6]: the pixels ``dump_sample_index`` picks, a fixed seeded choice in ascending
+pixel order; ``dump_outputs`` has the rule, the result line's ``dumped_outputs`` names what was written).  Inputs
+and weights are seeded, so two builds run with the same arguments can be compared output for output.
+
+The engine normally times every conv shape's tactics when it is built, and two runs whose noisy timings pick
+different tactics differ in the last bits of the disparity (and, where the disparity is near zero, by any amount in
+the reprojected cloud).  For the workloads with a plan under ``bench_plans/`` (the default one) bench.py therefore
+pins that committed plan instead: every run launches the same kernels and writes the same outputs, and nothing is
+tuned (``plan_source`` in the result line).  ``--tune`` restores the tuner; ``--export-plan FILE`` writes the plan
+the engine launched, which is how a committed plan is refreshed after the tactics change.
 """
 from __future__ import annotations
 
@@ -63,10 +78,89 @@ def parse(argv=None):
     p.add_argument("--width", type=int, default=640)
     p.add_argument("--iters", type=int, default=-1, help="override GRU iterations (tests only)")
     p.add_argument("--latency-frames", type=int, default=20)
-    p.add_argument("--no-latency", action="store_true")
+    p.add_argument("--no-latency", action="store_true", help="with --full: skip the batch-1 latency block")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: the all-gather alone, batch-1 latency per preset")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy (float32, DUMP_BUDGET bytes at most)")
+    p.add_argument("--tune", action="store_true",
+                   help="time the conv tactics on this GPU instead of pinning the committed plan of the workload")
+    p.add_argument("--export-plan", metavar="FILE", default=None,
+                   help="write the tactic plan the engine launched (rank 0), e.g. to refresh bench_plans/")
     p.add_argument("--device", choices=("gpu", "cpu"), default="gpu",
                    help="cpu = PyTorch-oracle rehearsal of the launcher/DP plumbing (gloo only, not a benchmark)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+PLAN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bench_plans")
+
+
+def committed_plan_path(args, arch: str = "gfx950") -> str | None:
+    """The committed tactic plan of this workload (model, per-GPU batch, size; default iterations only), if any."""
+    if args.iters > 0:
+        return None
+    path = os.path.join(PLAN_DIR, f"{args.model}_b{args.per_gpu_batch}_{args.height}x{args.width}_{arch}.plan")
+    return path if os.path.exists(path) else None
+
+
+def pin_committed_plan(path: str) -> int:
+    """Load the entries of a committed plan into the process's tactic table and pin them, so the engine built next
+    launches exactly these tactics whatever its tuner would measure and whatever plan file its cache holds: the
+    outputs are then the same in every run.  A shape the file lacks is still tuned.  Plan files carry the id of the
+    library build that timed them and the loader takes nothing from another build's; the committed entries name
+    tactics by number only, so they are handed over under this build's id.  Returns the entries loaded."""
+    import tempfile
+    from stereoalgorithms_amd import _native as N
+    lib = N.require_native()
+    with open(path) as f:
+        entries = [l for l in f if l.strip() and not l.startswith("#")]
+    fd, tmp = tempfile.mkstemp(suffix=".plan")
+    try:
+        with os.fdopen(fd, "w") as f:
+            f.write(f"# sa-plan build={lib.sa_plan_build_id().decode()}\n")
+            f.writelines(entries)
+        n = int(lib.sa_conv_plan_load(tmp.encode()))
+    finally:
+        os.unlink(tmp)
+    if n != len(entries):
+        raise RuntimeError(f"{path}: {n} of {len(entries)} plan entries accepted (tactic numbers of another build?)")
+    lib.sa_conv_plan_pin(1)
+    return n
+
+
+DUMP_BUDGET = 60_000_000  # bytes of array data --dump-outputs writes at most, over all files
+
+
+def dump_sample_index(n_rows: int, keep: int, seed: int = 0) -> np.ndarray:
+    """The ``keep`` of ``n_rows`` rows a sampled dump holds: a seeded choice without replacement, ascending, so it is
+    the same for every run and build."""
+    return np.sort(np.random.default_rng(seed).choice(n_rows, size=keep, replace=False))
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write ``arrays`` (name -> (float32 ndarray, row width in elements)) under ``out_dir``.  Every array whose
+    share of DUMP_BUDGET (what is left, split evenly over the arrays still to write) covers it is written whole as
+    ``<name>.npy``; a larger one as ``<name>_sample.npy`` holding the rows dump_sample_index picks.  Returns
+    name -> {file, shape, sampled_rows} for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    left, todo, written = DUMP_BUDGET, len(arrays), {}
+    for name, (a, width) in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        share, todo = left // todo, todo - 1
+        fname, sampled = f"{name}.npy", None
+        if a.nbytes > share:
+            rows = a.reshape(-1, width)
+            sampled = int(share // (width * 4))
+            a = rows[dump_sample_index(rows.shape[0], sampled)]
+            a = a.reshape(-1) if width == 1 else a
+            fname = f"{name}_sample.npy"
+        np.save(os.path.join(out_dir, fname), a)
+        left -= a.nbytes
+        written[name] = {"file": fname, "shape": list(a.shape), "sampled_rows": sampled}
+    return written
 
 
 def _free_port() -> int:
@@ -224,7 +318,7 @@ def main(argv=None) -> int:
 
     B, H, W = args.per_gpu_batch, args.height, args.width
     Q = np.array([[1, 0, 0, -W / 2], [0, 1, 0, -H / 2], [0, 0, 0, 500.0], [0, 0, 1 / 60.0, 0]], np.float32)
-    plan_digests = None
+    plan_digests = plan_file = plan_pinned = None
     if cpu:
         eng = OracleEngine(args.model, H, W, B, args.iters, seed=0)
         eng.set_Q(Q)
@@ -232,10 +326,23 @@ def main(argv=None) -> int:
         from stereoalgorithms_amd.models.engine import NativeStereoEngine
         # every rank runs rank 0's tactic plan (rank 0 tunes, the others build from its broadcast plan bytes), so
         # no rank's noisy timing picks a slower kernel that would set the job's step time
-        eng, plan_digests = build_engine_shared_plan(
-            lambda: NativeStereoEngine(args.model, None, H, W, batch=B, iters=args.iters, device=dev.index, seed=0),
-            world if (world > 1 or force_gather) else 1, rank)
+        # the workload's committed plan, pinned on every rank (--tune: this GPU's own timings decide instead, and two
+        # runs may then launch different tactics and differ in the last bits of their outputs)
+        plan_file = None if args.tune else committed_plan_path(args)
+        plan_pinned = pin_committed_plan(plan_file) if plan_file else None
+        try:
+            eng, plan_digests = build_engine_shared_plan(
+                lambda: NativeStereoEngine(args.model, None, H, W, batch=B, iters=args.iters, device=dev.index, seed=0),
+                world if (world > 1 or force_gather) else 1, rank)
+        finally:
+            if plan_file:
+                from stereoalgorithms_amd import _native as N
+                N.require_native().sa_conv_plan_pin(0)
         eng.set_Q(Q)
+        if args.export_plan and rank == 0:
+            err = eng.plan_export(args.export_plan)
+            if err:
+                raise OSError(err, f"could not write {args.export_plan}")
     # every rank reprojects its frames' point clouds in the frame graph and keeps them (the reference produces a
     # cloud per frame inside its timed region, RAFTStereo/src/TRTRAFTStereo.cpp:140-144)
     dp = DataParallelStereo(eng, world_size=world, rank=rank, force_gather=force_gather, cloud=True)
@@ -300,6 +407,17 @@ def main(argv=None) -> int:
         dist.all_gather(ts_all, t)
         rank_ms = [x.item() / args.steps * 1e3 for x in ts_all]
         dt = max(x.item() for x in ts_all)
+        gathered = [None] * world
+        dist.all_gather_object(gathered, ranks[0])
+        ranks = gathered
+    assert out.shape == (world * B, H, W) and torch.isfinite(out).all()
+    assert cloud is not None and cloud.shape == (B, H, W, 6)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the tensors the last timed step handed back (gathered disparity, this rank's clouds), before anything else
+        # runs on the engine
+        dumped = dump_outputs(args.dump_outputs, {"disparity": (out.cpu().numpy(), 1), "cloud": (cloud.cpu().numpy(), 6)})
+    if world > 1 and args.full:
         # the all-gather alone, outside the timed region (same message as one step's gather)
         send = out.new_empty((B, H, W))
         recv = out.new_empty((world * B, H, W))
@@ -316,11 +434,6 @@ def main(argv=None) -> int:
         g = torch.tensor([(time.perf_counter() - tg) / reps * 1e3], device=dev, dtype=torch.float64)
         dist.all_reduce(g, op=dist.ReduceOp.MAX)
         gather_ms = round(g.item(), 4)
-        gathered = [None] * world
-        dist.all_gather_object(gathered, ranks[0])
-        ranks = gathered
-    assert out.shape == (world * B, H, W) and torch.isfinite(out).all()
-    assert cloud is not None and cloud.shape == (B, H, W, 6)
 
     ms_step = dt / args.steps * 1e3
     fps = world * B * args.steps / dt
@@ -347,7 +460,7 @@ def main(argv=None) -> int:
         eng = None
 
     h2d = None if cpu else h2d
-    if rank == 0 and world == 1 and not args.no_latency and not cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_latency and not cpu:
         release_step()
         import tempfile
         from stereoalgorithms_amd.models.engine import NativeStereoEngine
@@ -460,11 +573,16 @@ def main(argv=None) -> int:
             "allgather_bytes_per_rank": B * H * W * 4,
             "point_clouds": f"per rank [{B},{H},{W},6] fp32 XYZRGB, reprojected in the frame graph, kept local",
             "plan": None if cpu else plan_b8,
+            # where the tactics came from: the committed plan (file under bench_plans/, entries pinned) or the tuner
+            "plan_source": None if cpu else ({"committed": os.path.basename(plan_file), "entries": plan_pinned}
+                                             if plan_file else "tuned"),
             # launched-tactic digests of every rank (None = some rank could not report one: unknown, not "equal")
             "plans_identical_across_ranks": (None if plan_digests is None or None in plan_digests
                                              else len(set(plan_digests)) == 1),
             "device_bytes": dev_bytes_b8,
             "latency_b1": extra,
+            "full": args.full,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(rec), flush=True)
     if world > 1 or force_gather:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regression gate: compare a fresh bench.py JSON line against the previous round's driver record.
+"""Regression gate: compare a fresh ``bench.py --full`` JSON line against the previous round's driver record.
 
     python3 tools/bench_regress.py gpurun_out/r5b/bench.log [--baseline BENCH_r04.json] [--tol 0.03]
 

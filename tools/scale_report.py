@@ -26,8 +26,9 @@ def run_one(n: int, bench_args: list[str], timeout: int) -> dict:
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     t0 = time.time()
     try:
-        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(n), "--no-latency", *bench_args],
-                           env=env, capture_output=True, text=True, timeout=timeout)
+        # --full for the all-gather-alone column, --no-latency to leave its batch-1 block out
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(n), "--full", "--no-latency",
+                            *bench_args], env=env, capture_output=True, text=True, timeout=timeout)
     except subprocess.TimeoutExpired:
         return {"n": n, "error": f"timeout after {timeout}s"}
     wall = time.time() - t0
